@@ -20,6 +20,12 @@ The JSON also carries device-time phases per round (HIP events, min / max over r
 overlapped (hidden) side-stream time, process-start-to-end latency (the reference's "Latency"),
 and with N > 1 the measured mailbox post bandwidth, staleness and verification counts.
 
+A plain run sets up, warms up, times the rounds and prints the result line. ``--full`` adds what
+the headline figure does not need (N > 1: the information-passing measurement and the cross-rank
+ledger audit after the timed rounds). ``--dump-outputs DIR`` writes what the last timed round
+computed as ``DIR/*.npy`` (data, initial weights and the loopback lags are seeded: the same
+arguments give the same inputs in every run).
+
     python bench.py                                   # 1 GPU, 8 virtual clients
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
 """
@@ -63,7 +69,10 @@ def parse():
     ap.add_argument("--sync", action="store_true", help="synchronous gossip instead of async")
     ap.add_argument("--no-ledger", action="store_true")
     ap.add_argument("--no-ckpt", action="store_true")
-    ap.add_argument("--out", default=None)
+    ap.add_argument("--out", default=None,
+                    help="directory for the run's ledger, metrics and checkpoints (default: "
+                         "runs/bench/n<N> under the working directory; under the temporary "
+                         "directory where that cannot be written)")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--lanes", type=int, default=0, help="concurrent client lanes per GPU (0 = auto)")
     ap.add_argument("--transport", default="auto",
@@ -73,8 +82,16 @@ def parse():
     ap.add_argument("--overlap-wgrad", type=int, default=-1, help="1/0 force, -1 auto")
     ap.add_argument("--anomaly-filter", default=None,
                     help="override the preset's update anomaly filter (none|pagerank|modz|both)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed rounds also run what the headline figure does not need: "
+                         "the information-passing measurement (N > 1) and the cross-rank ledger "
+                         "audit / final-model check (N > 1)")
     ap.add_argument("--no-info-passing", action="store_true",
-                    help="skip the post-run information-passing measurement (N > 1)")
+                    help="with --full: skip the post-run information-passing measurement (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed rounds write what the last round computed (the hosted "
+                         "models' fp32 master parameters, sampled at fixed seeded positions, and "
+                         "the round's loss / accuracy figures) as DIR/<name>.npy")
     ap.add_argument("--global-test-samples", type=int, default=0,
                     help="override the global evaluation draw (experiments only; 0 = preset)")
     ap.add_argument("--batch-size", type=int, default=0,
@@ -197,6 +214,67 @@ def _async_mix_desc(fed) -> str:
     return d
 
 
+def _default_out(world: int) -> str:
+    """Where the run's ledger, metrics and checkpoints go without ``--out``: ``runs/bench/n<N>``
+    under the working directory, or, where that cannot be written (a read-only checkout, another
+    user's tree), the same layout under the temporary directory, per user. Every rank of a job
+    sees the same file system and arrives at the same answer."""
+    import tempfile
+    rel = os.path.join("runs", "bench", f"n{world}")
+    user = os.getuid() if hasattr(os, "getuid") else "user"
+    for out in (rel, os.path.join(tempfile.gettempdir(), f"bcfl-{user}", rel)):
+        try:
+            os.makedirs(out, exist_ok=True)
+            with tempfile.TemporaryFile(dir=out):
+                pass
+            return out
+        except OSError:
+            continue
+    raise SystemExit(f"bench.py: cannot write {rel} here or under {tempfile.gettempdir()}; pass --out DIR")
+
+
+DUMP_SAMPLE_BYTES = 32 << 20  # --dump-outputs: fp32 bytes of sampled parameters over all models
+DUMP_SEED = 20240607
+
+
+def _dump_outputs(fed, out_dir: str, last: dict) -> None:
+    """``--dump-outputs DIR``: what the last timed round left its caller. ``model_<name>.npy``:
+    the fp32 master parameters of every model this rank hosts after the round (server FedAvg: the
+    global model; serverless: each hosted client's model), a model above the sample size at
+    fixed positions drawn once from ``DUMP_SEED`` (sorted, the same in every run and for every
+    model, so two builds compare element for element). ``round_metrics.npy``: float64
+    ``[train_loss, global_acc, global_loss]`` of that round as ``run_round`` returned them (NaN =
+    not evaluated); ``accuracy_curve.npy``: the per-round global accuracies up to it."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if fed.global_master is not None:
+        models = {"global": fed.global_master}
+    elif fed.multi:
+        models = {f"client{c}": fed.client_master[c] for c in fed.local_clients}
+    else:
+        models = {f"client{fed.local_clients[0]}": fed.flat.master}
+    numel = int(fed.flat.master.numel())
+    n_models = 1 if fed.global_master is not None else int(fed.cfg.num_clients)
+    keep = DUMP_SAMPLE_BYTES // 4 // max(n_models, 1)
+    idx = None
+    if numel > keep:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, numel, size=keep))
+        idx = torch.from_numpy(pos).to(fed.flat.master.device)
+    for name, m in models.items():
+        v = m.detach().reshape(-1)
+        v = v if idx is None else v.index_select(0, idx)
+        np.save(os.path.join(out_dir, f"model_{name}.npy"), v.float().cpu().numpy())
+    if fed.rt.is_main:
+        def f(x):
+            return float("nan") if x is None else float(x)
+        np.save(os.path.join(out_dir, "round_metrics.npy"),
+                np.array([f(last.get("train_loss")), f(last.get("global_acc")),
+                          f(last.get("global_loss"))], dtype=np.float64))
+        np.save(os.path.join(out_dir, "accuracy_curve.npy"),
+                np.array([f(x) for x in fed.global_accuracies], dtype=np.float64))
+
+
 def _rehearsal_cu_split() -> None:
     """``BCFL_REHEARSE_CUS=<compute units>``: ranks REHEARSED on one GPU each get a disjoint 1/N of
     its compute units (ROCr's ``HSA_CU_MASK``, set before the runtime initialises), so N processes
@@ -230,7 +308,7 @@ def main():
     if rt.world != a.gpus:
         raise SystemExit(f"bench.py --gpus {a.gpus} but the job has WORLD_SIZE={rt.world}: "
                          "launch one rank per GPU (torch.distributed.run --nproc-per-node N)")
-    out = a.out or os.path.join("runs", "bench", f"n{rt.world}")
+    out = a.out or _default_out(rt.world)
     transport = a.transport
     if transport == "auto" and a.mode == "serverless" and not a.sync:
         # N = 1: the 8 clients run the SAME asynchronous protocol as on 8 GPUs (delta exchange,
@@ -337,8 +415,10 @@ def main():
     # peer over xGMI), read before finish() closes the transport
     tr = getattr(fed.gossip, "transport", None)
     p2p = tr.post_stats() if tr is not None and hasattr(tr, "post_stats") else None
+    if a.dump_outputs:
+        _dump_outputs(fed, a.dump_outputs, last)
     info = None
-    if rt.world > 1 and not a.no_info_passing:
+    if a.full and rt.world > 1 and not a.no_info_passing:
         # outside the timed rounds: one client's model (the wire payload of the gossip engine)
         # from rank 0 to every peer over the mailbox transport, sequential (sync) vs concurrent
         # (async), measured and predicted, before / after PageRank removal
@@ -347,7 +427,8 @@ def main():
             info = measure(fed.flat.numel, sources=[0], iters=3)
         except Exception as e:  # mailbox setup failures are agreed on every rank
             info = {"error": f"{type(e).__name__}: {e}"}
-    fed.finish()
+    # --full: the cross-rank ledger audit / final-model comparison (collectives, N > 1) run too
+    fed.finish(audit=a.full)
     if rt.is_main:
         rec = {
             "metric": metric_name(cfg),
@@ -359,6 +440,7 @@ def main():
             "ms_per_step": s_per_round * 1000.0,
             "higher_is_better": False,
             "scaling": "strong",
+            "full": bool(a.full),
             "vs_baseline": s_per_round / BASELINE_S_PER_ROUND,
             "speedup_vs_baseline": BASELINE_S_PER_ROUND / s_per_round,
             "baseline_s_per_round": BASELINE_S_PER_ROUND,

@@ -6,7 +6,7 @@ OUT=${OUT:-gpurun_out/infopass}
 mkdir -p $OUT
 export BCFL_DIST_BACKEND=gloo
 for n in "$@"; do
-  timeout -k 10 300 python -u bench.py --gpus $n --steps 4 --warmup 2 > $OUT/n$n.json 2> $OUT/n$n.err || { echo "n$n rc=$?"; tail -20 $OUT/n$n.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --gpus $n --steps 4 --warmup 2 > $OUT/n$n.json 2> $OUT/n$n.err || { echo "n$n rc=$?"; tail -20 $OUT/n$n.err; exit 1; }
   python3 - $OUT/n$n.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

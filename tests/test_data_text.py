@@ -1,10 +1,41 @@
-"""Real-text path: reference CSVs + offline WordPiece (skipped when the CSVs are not mounted)."""
+"""Real-text path: reference CSVs + offline WordPiece. The three CSVs are stored gzip-compressed
+under ``tests/golden/dataset`` and unpacked into a temporary ``$BCFL_DATA_DIR`` for this module."""
+import glob
+import gzip
+import os
+import shutil
+
 import numpy as np
 import pytest
 
 from bcfl.data import text
 
-pytestmark = pytest.mark.skipif(not text.available("medical_csv"), reason="reference CSVs not mounted")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dataset")
+
+
+def _forget_loaded():
+    from bcfl.data.registry import load_split
+    for f in (text._raw, text.tokenizer, load_split):
+        f.cache_clear()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def csv_dir(tmp_path_factory):
+    d = tmp_path_factory.mktemp("dataset")
+    packed = sorted(glob.glob(os.path.join(GOLDEN, "*.csv.gz")))
+    assert len(packed) == 3, packed
+    for p in packed:
+        with gzip.open(p, "rb") as src, open(d / os.path.basename(p)[:-len(".gz")], "wb") as dst:
+            shutil.copyfileobj(src, dst)
+    old = os.environ.get("BCFL_DATA_DIR")
+    os.environ["BCFL_DATA_DIR"] = str(d)
+    _forget_loaded()
+    yield str(d)
+    if old is None:
+        os.environ.pop("BCFL_DATA_DIR", None)
+    else:
+        os.environ["BCFL_DATA_DIR"] = old
+    _forget_loaded()
 
 
 def test_medical_csv_split_shapes_and_labels():
